@@ -186,6 +186,24 @@ def pipeline_leg(trainer, device, batch, patch, steps):
             "value": round(batch / dt, 3), "unit": "patches/s", "ms_per_step": round(dt * 1e3, 3)}
 
 
+DUMP_SAMPLE = 1 << 22   # entries of each flat 35.6 M-entry buffer written by --dump-outputs (16 MB of float32 each)
+
+
+def dump_outputs(out_dir, loss, trainer):
+    """What the last timed step handed its caller, as float32 .npy files: the loss it returned (whole) and the parameters
+    and the gradient it left in the flat buffers (the AdamW update is in place) as a fixed, seeded sample of DUMP_SAMPLE
+    entries - the same indices in every run, so two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = trainer.opt.param.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    arrays = {"loss": loss.detach().reshape(1).cpu().numpy(),
+              "params_sample": trainer.opt.param.detach().cpu().numpy()[idx],
+              "grad_sample": trainer.opt.grad.detach().cpu().numpy()[idx]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(name + ".npy" for name in arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -200,7 +218,12 @@ def main():
                     help="skip the inference (config 2) and tiled 512x512 (config 4) legs (rank 0, after the timed region)")
     ap.add_argument("--patch", type=int, default=128)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss; seeded sample of the parameters and "
+                         "gradient) to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from promptir_amd import ops
     from promptir_amd.train import DataParallelTrainer, init_distributed
@@ -249,6 +272,7 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    dumped = dump_outputs(args.dump_outputs, loss, trainer) if args.dump_outputs and rank == 0 else None
 
     # BASELINE config 5 (DDP, batch 8 per GPU) beside the headline line: same trainer, graph re-captured for the shape
     config5 = None
@@ -452,6 +476,8 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu, "config5": config5, "inference": inference, "tiled_512": tiled,
             "input_pipeline": pipeline,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

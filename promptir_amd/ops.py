@@ -1426,12 +1426,13 @@ class _SideWgrads:
         self.main = torch.cuda.current_stream(device)
         self.side = None
         if _side_stream_enabled() and lib.records is None:   # the instrumented (timed) step stays on one stream
-            # Side streams under ONE capturing stream are fine (the trainer's single-stream graph does it).  Under a
-            # capture that spans SEVERAL part streams, each forking its own side stream, the round-3 build died with a
-            # host segfault inside graph capture (each wgrad forks + joins a fourth-level stream, records
-            # its operands on it - block frees of a capturing pool are deferred per recorded stream - and creates
-            # two events per call; with two origin streams the capture held ~190 cross-stream edges per part).  The
-            # fault was never bisected on hardware; the combination is refused instead of risked:
+            # Inside a stream capture the weight gradients stay on the capturing stream.  Under a capture that spans
+            # SEVERAL part streams, each forking its own side stream, the round-3 build died with a host segfault inside
+            # graph capture (each wgrad forks + joins a fourth-level stream, records its operands on it -
+            # block frees of a capturing pool are deferred per recorded stream - and creates two events per call; with
+            # two origin streams the capture held ~190 cross-stream edges per part): that combination is refused.  With
+            # ONE origin stream the fork / join diamonds capture, but replaying the graph segfaults in the host runtime
+            # (hipGraphLaunch; the trainer's graph=True, micro_streams=1 step), so no side stream is forked there either.
             if torch.cuda.is_current_stream_capturing():
                 _CAPTURE_MAINS.add(self.main.cuda_stream)
                 if len(_CAPTURE_MAINS) > 1:
@@ -1441,10 +1442,10 @@ class _SideWgrads:
                         "ops.side_streams(False) or capture on a single stream")
             else:
                 _CAPTURE_MAINS.clear()
-            key = (device.index, self.main.cuda_stream)   # one side stream per main stream (two-stream training)
-            self.side = _SIDE_STREAMS.get(key)
-            if self.side is None:
-                self.side = _SIDE_STREAMS[key] = torch.cuda.Stream(device)
+                key = (device.index, self.main.cuda_stream)   # one side stream per main stream (two-stream training)
+                self.side = _SIDE_STREAMS.get(key)
+                if self.side is None:
+                    self.side = _SIDE_STREAMS[key] = torch.cuda.Stream(device)
         self.used = False
         self.pending = []
 
